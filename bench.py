@@ -13,6 +13,12 @@ Launch:  python bench.py [--gpus 1 --steps 3 --warmup 1]
          python bench.py --gpus N ...   (starts the N ranks itself: a child torch.distributed.run)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Prints ONE JSON line on rank 0.  --gpus must equal WORLD_SIZE when a launcher set it.
+
+A plain run sets the scene up, warms up, times --steps frames and prints the headline
+(metric, value, unit, ms_per_step, config).  --full adds everything that takes runs of
+its own: the counted frame behind the roofline figures and `stats`, the per-kernel split,
+the first-render frame and the CPU baseline.  --dump-outputs DIR writes the film of the
+last timed step (what a caller of the timed path receives) as DIR/film.npy on rank 0.
 """
 import argparse
 import json
@@ -73,6 +79,12 @@ def parse():
                     help="N > 1: after the warm-up, re-deal the blocks by the work each shaded (path-bounces "
                          "summed over ranks, hpt_set_block_weights); off: the Hilbert-cyclic deal")
     ap.add_argument("--workdir", default=os.path.join(tempfile.gettempdir(), "hpt_bench"))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the counted frame (roofline figures, stats), the "
+                         "per-kernel split, the first-render frame and the CPU baseline (see --cpu-baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's RGBW film (float32, H x W x 4, the "
+                         "reduced frame on rank 0) as DIR/film.npy")
     return ap.parse_args()
 
 
@@ -186,6 +198,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     world = check_world(args.gpus, os.environ)
@@ -266,15 +280,19 @@ def main():
                                    spp=spp, width=W, height=H, frames=1)
         step(1)
         balanced = True
-    # one untimed counted frame: traversal counters for the byte model (the
-    # render is deterministic, so every frame has exactly these counts)
-    step(2)
-    c = r.stats()
-    frame = dict(nodes=c.nodes, bnodes=c.binary_nodes, prims=c.prims, exact=c.prim_exact, closest=c.closest_rays, shadow=c.shadow_rays,
-                 unocc=c.shadow_unoccluded, bounces=c.bounces, launches=c.trace_launches,
-                 node_slots=c.node_slots, prim_slots=c.prim_slots,
-                 p_rays=c.packet_rays, p_nodes=c.packet_nodes, p_prims=c.packet_prims, p_exact=c.packet_exact,
-                 p_node_slots=c.packet_node_slots, p_prim_slots=c.packet_prim_slots, p_fallbacks=c.packet_fallbacks)
+    frame = None
+    if args.full:
+        # one untimed counted frame: traversal counters for the byte model (the
+        # render is deterministic, so every frame has exactly these counts)
+        step(2)
+        c = r.stats()
+        frame = dict(nodes=c.nodes, bnodes=c.binary_nodes, prims=c.prims, exact=c.prim_exact,
+                     closest=c.closest_rays, shadow=c.shadow_rays,
+                     unocc=c.shadow_unoccluded, bounces=c.bounces, launches=c.trace_launches,
+                     node_slots=c.node_slots, prim_slots=c.prim_slots,
+                     p_rays=c.packet_rays, p_nodes=c.packet_nodes, p_prims=c.packet_prims, p_exact=c.packet_exact,
+                     p_node_slots=c.packet_node_slots, p_prim_slots=c.packet_prim_slots,
+                     p_fallbacks=c.packet_fallbacks)
     acc = {"ms_trace": 0.0, "ms_packet": 0.0, "launches": 0, "p_launches": 0, "kernels": {}}
 
     def collect():
@@ -287,6 +305,55 @@ def main():
         acc["p_launches"] += s.packet_launches
 
     dt = timed_steps(lambda: step(3), args.steps, world, dist, torch.cuda.synchronize, "cuda:%d" % local, collect)
+    if args.dump_outputs and rank == 0:
+        # the film of the last timed step, before any --full frame overwrites it
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "film.npy"), film.cpu().numpy().astype(np.float32, copy=False))
+    workload = "%s %dx%d @ %d spp, maxDepth %d, %d strands / %d segments" % (
+        args.config, W, H, spp, max_depth, n, info.segments)
+    paths_total = W * H * spp * args.steps
+    value = paths_total / dt / 1e6
+    full = None
+    if args.full:
+        full = full_figures(args, r, step, frame, acc, dt, film, world, rank, "cuda:%d" % local, W, H, cfg, defines,
+                            hair_src, workload, paths_total)
+    if rank == 0:
+        out = {
+            "metric": "Mpaths/sec + achieved HBM GB/s, furball Marschner 512² @ 256spp",
+            "value": round(value, 3),
+            "unit": "Mpaths/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32 (f64 cylinder tests)",
+            "data": "synthetic hair (seeded, BINARY_HAIR; reference hair blobs absent) lit by the scene's sunsky (Hosek-Wilkie sky + Preetham sun rasterised like sunsky.cpp)",
+            "config": {"workload": workload,
+                       "paths_per_step": W * H * spp, "parallelism": "tiles%d" % world,
+                       "gpus_arg": args.gpus, **pg,
+                       "deal": "work-balanced (warm-up frame's path-bounces per block)" if balanced
+                       else "Hilbert-cyclic 32x32 blocks",
+                       **({"rehearsal": "HPT_BENCH_BACKEND=gloo: ranks share GPUs, host-copy reduce"}
+                          if host_film is not None and world > 1 else {}),
+                       "kd_nodes": int(info.kd_nodes), "kd_depth": int(info.kd_depth),
+                       "prepare_s": round(t_prep, 3)},
+            "full": args.full,
+        }
+        if full is not None:
+            out.update(full)
+        print(json.dumps(out), flush=True)
+    r.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_figures(args, r, step, frame, acc, dt, film, world, rank, device, W, H, cfg, defines, hair_src, workload,
+                 paths_total):
+    """--full: everything beyond the headline that takes frames or runs of its own (every rank renders
+    the frames; rank 0 returns the extra sections of the result line, the others None)."""
     # the per-kernel split, averaged over three more (untimed) frames with an event around every
     # kernel (the timed steps carry events around the traversal launches only: collect_stats 3)
     split_frames = 3
@@ -299,16 +366,12 @@ def main():
     # or the CLI's first pass does: every bounce's queue length read back); not
     # part of `value`, which times repeated frames of the same spp range
     r.clear_schedules()
-    first_ms = 1e3 * timed_steps(lambda: step(1), 1, world, dist, torch.cuda.synchronize, "cuda:%d" % local)
+    first_ms = 1e3 * timed_steps(lambda: step(1), 1, world, dist, torch.cuda.synchronize, device)
     assert r.stats().waves_ahead == 0
     ms_trace, ms_packet, launches, p_launches = acc["ms_trace"], acc["ms_packet"], acc["launches"], acc["p_launches"]
     ms_kernels = acc["kernels"]
     tot = {k: v * args.steps for k, v in frame.items()}
 
-    workload = "%s %dx%d @ %d spp, maxDepth %d, %d strands / %d segments" % (
-        args.config, W, H, spp, max_depth, n, info.segments)
-    paths_total = W * H * spp * args.steps
-    value = paths_total / dt / 1e6
     io = BYTES_CLOSEST * tot["closest"] + BYTES_SHADOW * tot["shadow"] + BYTES_UNOCC * tot["unocc"]
     bytes_alg = io + B8D_NODE * tot["bnodes"] + (B8D_REF + B8D_PRIM) * tot["prims"]
     bytes_lay = io + BYTES_NODE4 * tot["nodes"] + BYTES_PRIM * tot["prims"] + BYTES_EXACT * tot["exact"]
@@ -353,27 +416,6 @@ def main():
             cpu = cpu_baseline(args, cfg, defines, hair_src, None, nodes, idx)
         img = native.develop(film.cpu().numpy())
         out = {
-            "metric": "Mpaths/sec + achieved HBM GB/s, furball Marschner 512² @ 256spp",
-            "value": round(value, 3),
-            "unit": "Mpaths/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32 (f64 cylinder tests)",
-            "data": "synthetic hair (seeded, BINARY_HAIR; reference hair blobs absent) lit by the scene's sunsky (Hosek-Wilkie sky + Preetham sun rasterised like sunsky.cpp)",
-            "config": {"workload": workload,
-                       "paths_per_step": W * H * spp, "parallelism": "tiles%d" % world,
-                       "gpus_arg": args.gpus, **pg,
-                       "deal": "work-balanced (warm-up frame's path-bounces per block)" if balanced
-                       else "Hilbert-cyclic 32x32 blocks",
-                       **({"rehearsal": "HPT_BENCH_BACKEND=gloo: ranks share GPUs, host-copy reduce"}
-                          if host_film is not None and world > 1 else {}),
-                       "kd_nodes": int(info.kd_nodes), "kd_depth": int(info.kd_depth),
-                       "prepare_s": round(t_prep, 3)},
             # bound: the roofline the kernel is priced against (HBM: no dense contraction here);
             # limiter: what the PMC counters say actually holds it below that roofline
             "roofline": {"bound": "hbm", "limiter": limiter, "kernel": "k_trace", "achieved": round(achieved, 1),
@@ -442,10 +484,7 @@ def main():
                       # identical for every traversal variant, since hits are bit-exact
                       "film_fingerprint": float(film.double().sum().item())},
         }
-        print(json.dumps(out), flush=True)
-    r.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

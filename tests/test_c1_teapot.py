@@ -11,9 +11,10 @@ prepares the same scene with its own loader (csrc/host/mesh.cpp); its device ren
 (k_mesh_paths) is checked against the oracle in tests/test_gpu_c1.py.
 
 The reference does not ship models/Mesh00{0,1}.obj: tests/teapot_meshes.py
-writes seeded stand-ins.  The scene file and its envmap are read from
-/root/reference at test time (this file is CPU-only; the GPU box has no
-reference tree); no pixel of a reference render exists for these meshes, so
+writes seeded stand-ins.  The scene file and its envmap are the fixtures
+under tests/golden/teapot (scene.xml as the reference ships it, the envmap at
+half resolution: tests/golden/extract_teapot.py), so this file needs nothing
+outside the repository; no pixel of a reference render exists for these meshes, so
 the render is checked for determinism and by geometric probes -- parity of the
 mesh path against the reference is unpinned beyond the unit pins below.
 """
@@ -33,9 +34,7 @@ from mitsuba_amd import native
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "oracle"))
 import film as ref  # noqa: E402
 
-REF_TEAPOT = "/root/reference/models/teapot"
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF_TEAPOT, "scene.xml")),
-                                reason="the reference's teapot scene is only present in the build container")
+REF_TEAPOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "teapot")
 
 W = H = 64
 SPP = 16

@@ -16,11 +16,12 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--config", "straight_kk", "--width", "160", "--height", "96", "--spp", "16", "--steps", "2",
-        "--warmup", "1", "--cpu-baseline", "off"]
+        "--warmup", "1", "--full", "--cpu-baseline", "off"]
 
 
 def _port():
@@ -40,7 +41,7 @@ def _lines(res):
 def test_bench_two_ranks_reduce_the_one_rank_frame(tmp_path):
     env = dict(os.environ, HPT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     one = _lines(subprocess.run([sys.executable, "bench.py", "--gpus", "1",
-                                 "--workdir", str(tmp_path / "w1")] + ARGS,
+                                 "--workdir", str(tmp_path / "w1"), "--dump-outputs", str(tmp_path / "d1")] + ARGS,
                                 cwd=ROOT, env=env, capture_output=True, text=True, timeout=240))
     two = _lines(subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                                  "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
@@ -63,5 +64,9 @@ def test_bench_two_ranks_reduce_the_one_rank_frame(tmp_path):
         b["stats"]["film_fingerprint"])
     fa, fb = a["stats"]["film_fingerprint"], b["stats"]["film_fingerprint"]
     assert fa > 0 and abs(fa - fb) <= 1e-6 * fa, (fa, fb)
+    # --dump-outputs: the last timed step's film, the frame the fingerprint sums
+    film = np.load(tmp_path / "d1" / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (96, 160, 4)
+    assert abs(float(film.astype(np.float64).sum()) - fa) <= 1e-6 * fa
     # rank 0's own counters (its shard's camera rays) cover part of the frame
     assert 0 < b["stats"]["camera_rays_packet"] < a["stats"]["camera_rays_packet"]
