@@ -119,7 +119,12 @@ struct SceneDesc {
     /* film */
     int width = 768, height = 576;
     FilmDesc film;
+    /* the film's reconstruction filter and its parameters (box: radius; gaussian: stddev; mitchell:
+       B, C; lanczos: lobes -- a negative value is the plugin's default).  A <film> without an
+       <rfilter> parses to "gaussian" (film.cpp:90-94); a scene described through the low-level
+       setters keeps the tent */
     std::string rfilter = "tent";
+    float rfilterP0 = -1.0f, rfilterP1 = -1.0f;
     /* hair shapes (hair.cpp:609-640), each referencing one of bsdfs */
     std::vector<HairShapeDesc> shapes;
     std::vector<MeshShapeDesc> meshes;
@@ -260,7 +265,15 @@ void setupCamera(const SceneDesc &d, HptCamera &cam);      /* perspective.cpp:12
    built in float exactly as the reference (Transform products + Gauss-Jordan inverse) */
 bool cameraSampleToCamera(const SceneDesc &d, float s2c[16]);
 float cameraXFov(const SceneDesc &d);                       /* sensor.cpp:237-305 */
-void setupTent(float *lut, float &scale);                 /* rfilter.cpp:38-56 */
+/* the reconstruction filters (the plugins of src/rfilters), numbered like hairpt.h's HPT_RFILTER_* */
+enum { HPT_FILTER_BOX = 0, HPT_FILTER_TENT, HPT_FILTER_GAUSSIAN, HPT_FILTER_MITCHELL, HPT_FILTER_CATMULLROM,
+       HPT_FILTER_LANCZOS, HPT_FILTER_TYPES };
+extern const char *const kFilterNames[HPT_FILTER_TYPES];
+int filterTypeOf(const std::string &name);                  /* -1: no such plugin */
+/* ReconstructionFilter::configure (rfilter.cpp:37-55) of plugin `type` with parameters p0 / p1
+   (negative: the plugin's default): the 32-entry LUT, its scale, the radius and the border */
+bool setupFilter(int type, float p0, float p1, float *lut, float &scale, float &radius, int &border,
+                 std::string &err);
 
 /* Matrix4x4::invert (matrix.inl:138-190): float Gauss-Jordan with full pivoting, row-major */
 bool invertMatrix4(const float src[16], float out[16]);

@@ -11,8 +11,8 @@
  *   Kajiya-Kay (kajiyakay.cpp:80-107): energy conservation + sampling weight.
  *   Environment map (envmap.cpp:244-314): fp16 texels, luminance*sin(theta)
  *     marginal/conditional CDFs, normalisation.
- *   Camera (perspective.cpp:125-165, sobol.cpp:147-158), tent filter LUT
- *     (rfilter.cpp:38-56).
+ *   Camera (perspective.cpp:125-165, sobol.cpp:147-158), the reconstruction
+ *     filters' LUT (rfilter.cpp:37-55 over the six plugins of src/rfilters).
  *
  * All arithmetic is single precision in the reference's operation order,
  * compiled without FMA contraction, so the device consumes the same table
@@ -953,13 +953,95 @@ void setupCamera(const SceneDesc &d, HptCamera &cam) {
     cam.logRes = lg - 1;
 }
 
-void setupTent(float *lut, float &scale) {
+const char *const kFilterNames[HPT_FILTER_TYPES] = {"box", "tent", "gaussian", "mitchell", "catmullrom", "lanczos"};
+
+int filterTypeOf(const std::string &name) {
+    for (int t = 0; t < HPT_FILTER_TYPES; ++t)
+        if (name == kFilterNames[t]) return t;
+    return -1;
+}
+
+namespace {
+/* the Mitchell-Netravali cubic as mitchell.cpp:55-69 and catmullrom.cpp:40-55 write it (the
+   integer factors convert to float one by one, as in the reference's expression) */
+float mitchellEval(float x, float B, float C) {
+    x = std::abs(x);
+    float x2 = x * x, x3 = x2 * x;
+    if (x < 1) return 1.0f / 6.0f * ((12 - 9 * B - 6 * C) * x3 + (-18 + 12 * B + 6 * C) * x2 + (6 - 2 * B));
+    else if (x < 2)
+        return 1.0f / 6.0f * ((-B - 6 * C) * x3 + (6 * B + 30 * C) * x2 + (-12 * B - 48 * C) * x + (8 * B + 24 * C));
+    return 0.0f;
+}
+} // namespace
+
+/* ReconstructionFilter::configure (rfilter.cpp:37-55) over each plugin's constructor and eval
+   (src/rfilters/{box,tent,gaussian,mitchell,catmullrom,lanczos}.cpp), in float like the
+   reference's SINGLE_PRECISION build.  p0 / p1 are the plugin's parameters (box: radius;
+   gaussian: stddev; mitchell: B, C; lanczos: lobes), a negative value its default.  A radius
+   <= 0 (the reference's Assert, rfilter.cpp:38) or a border above HPT_MAX_FILTER_BORDER (no
+   k_splat / k_gather instantiation) fails with a message. */
+bool setupFilter(int type, float p0, float p1, float *lut, float &scale, float &radius, int &border,
+                 std::string &err) {
     const int R = HPT_FILTER_RES;
-    const float radius = 1.0f;
+    if (type < 0 || type >= HPT_FILTER_TYPES) {
+        err = "rfilter type " + std::to_string(type) + " is not one of box, tent, gaussian, mitchell, catmullrom, lanczos";
+        return false;
+    }
+    float stddev = 0.5f, mB = 1.0f / 3.0f, mC = 1.0f / 3.0f;
+    switch (type) {
+    case HPT_FILTER_BOX: radius = (p0 < 0 ? 0.5f : p0) + 1e-5f; break; /* box.cpp:38 */
+    case HPT_FILTER_TENT: radius = 1.0f; break;                         /* tent.cpp:34 */
+    case HPT_FILTER_GAUSSIAN:                                           /* gaussian.cpp:35-38 */
+        if (!(p0 < 0)) stddev = p0;
+        radius = 4 * stddev;
+        break;
+    case HPT_FILTER_MITCHELL: /* mitchell.cpp:35-39 */
+        radius = 2.0f;
+        if (!(p0 < 0)) mB = p0;
+        if (!(p1 < 0)) mC = p1;
+        break;
+    case HPT_FILTER_CATMULLROM: radius = 2.0f; break;                   /* catmullrom.cpp:32 */
+    default: radius = (float) (p0 < 0 ? 3 : (int) p0); break;           /* lanczos.cpp:35 getInteger("lobes", 3) */
+    }
+    char b[200];
+    /* (the box's 1e-5 must not turn a zero radius into a filter that no sample reaches) */
+    if (!(radius > 0) || !std::isfinite(radius) || (type == HPT_FILTER_BOX && p0 == 0)) {
+        std::snprintf(b, sizeof(b), "rfilter \"%s\": radius %g must be positive and finite", kFilterNames[type], radius);
+        err = b;
+        return false;
+    }
+    border = (int) std::ceil(radius - 0.5f);
+    if (border < 1) border = 1; /* a radius <= 0.5 touches the sample's own pixel only: the 3x3 kernels hold it */
+    if (border > HPT_MAX_FILTER_BORDER) {
+        std::snprintf(b, sizeof(b), "rfilter \"%s\": radius %g gives a border of %d pixels, above the device film's "
+                      "limit of %d (radius <= %g)", kFilterNames[type], radius, border, HPT_MAX_FILTER_BORDER,
+                      HPT_MAX_FILTER_BORDER + 0.5);
+        err = b;
+        return false;
+    }
+    auto eval = [&](float x) -> float {
+        switch (type) {
+        case HPT_FILTER_BOX: return std::abs(x) <= radius ? 1.0f : 0.0f;                  /* box.cpp:46-48 */
+        case HPT_FILTER_TENT: return std::max(0.0f, 1.0f - std::abs(x / radius));         /* tent.cpp:42-44 */
+        case HPT_FILTER_GAUSSIAN: {                                                        /* gaussian.cpp:52-57 */
+            float alpha = -1.0f / (2.0f * stddev * stddev);
+            return std::max(0.0f, std::exp(alpha * x * x) - std::exp(alpha * radius * radius)); /* fastexp = expf, math.h:201 */
+        }
+        case HPT_FILTER_MITCHELL: return mitchellEval(x, mB, mC);
+        case HPT_FILTER_CATMULLROM: return mitchellEval(x, 0.0f, 0.5f);
+        default: {                                                                         /* lanczos.cpp:43-55 */
+            x = std::abs(x);
+            if (x < 1e-4f) return 1.0f; /* Epsilon (constants.h:28) */
+            else if (x > radius) return 0.0f;
+            float x1 = 3.14159265358979323846f * x; /* M_PI under SINGLE_PRECISION (constants.h:80) */
+            float x2 = x1 / radius;
+            return (std::sin(x1) * std::sin(x2)) / (x1 * x2);
+        }
+        }
+    };
     float sum = 0.0f;
     for (int i = 0; i < R; ++i) {
-        float x = (radius * i) / R;
-        float v = std::max(0.0f, 1.0f - std::abs(x / radius));
+        float v = eval((radius * i) / R);
         lut[i] = v;
         sum += v;
     }
@@ -968,6 +1050,7 @@ void setupTent(float *lut, float &scale) {
     sum *= 2 * radius / R;
     float norm = 1.0f / sum;
     for (int i = 0; i < R; ++i) lut[i] *= norm;
+    return true;
 }
 
 } // namespace hpt

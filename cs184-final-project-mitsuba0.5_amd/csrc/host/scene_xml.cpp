@@ -631,12 +631,41 @@ void parseObject(Ctx &c, const XNode &nd, SceneDesc &d) {
                 if (fp.str.count("tonemapMethod")) fd.tonemapMethod = fp.str["tonemapMethod"];
                 std::string err;
                 if (!checkFilm(fd, err)) fail(c.file, k.line, err);
+                /* no <rfilter>: Film::configure instantiates a gaussian (film.cpp:90-94) */
+                d.rfilter = "gaussian";
+                d.rfilterP0 = d.rfilterP1 = -1.0f;
                 for (auto &fk : k.kids)
                     if (fk->tag == "rfilter") {
+                        /* the constructors of src/rfilters; other properties are ignored like
+                           Properties does with unqueried ones */
                         d.rfilter = attrS(c, *fk, "type");
-                        if (d.rfilter != "tent")
-                            fail(c.file, fk->line, "rfilter \"" + d.rfilter + "\" is not supported (only \"tent\")");
+                        d.rfilterP0 = d.rfilterP1 = -1.0f;
+                        const int type = filterTypeOf(d.rfilter);
+                        if (type < 0)
+                            fail(c.file, fk->line, "rfilter \"" + d.rfilter + "\" is not supported (box, tent, gaussian, "
+                                                   "mitchell, catmullrom, lanczos)");
+                        Props rp;
+                        collectProps(c, *fk, rp);
+                        auto param = [&](const char *name, float &out) {
+                            if (!rp.num.count(name)) return;
+                            out = num1(rp, name, -1.0f);
+                            /* negative values mean "the default" from hpt_set_rfilter down; none is
+                               a usable filter (a negative B / C cubic is not offered) */
+                            if (out < 0)
+                                fail(c.file, fk->line, "rfilter \"" + d.rfilter + "\": negative \"" + name + "\"");
+                        };
+                        if (type == HPT_FILTER_BOX) param("radius", d.rfilterP0);
+                        if (type == HPT_FILTER_GAUSSIAN) param("stddev", d.rfilterP0);
+                        if (type == HPT_FILTER_MITCHELL) param("B", d.rfilterP0), param("C", d.rfilterP1);
+                        if (type == HPT_FILTER_LANCZOS) param("lobes", d.rfilterP0);
                     }
+                {
+                    float lut[HPT_FILTER_RES + 1], scale, radius;
+                    int border;
+                    std::string ferr;
+                    if (!setupFilter(filterTypeOf(d.rfilter), d.rfilterP0, d.rfilterP1, lut, scale, radius, border, ferr))
+                        fail(c.file, k.line, ferr);
+                }
             }
         }
     } else if (tag == "bsdf") {
@@ -874,6 +903,23 @@ std::string sceneToJSON(const SceneDesc &d) {
     j.num("sampleCount", d.spp);
     j.str("film", d.film.type);
     j.str("rfilter", d.rfilter);
+    { /* the filter as configured: its radius, and the plugin's parameters with defaults resolved */
+        const int type = filterTypeOf(d.rfilter);
+        float lut[HPT_FILTER_RES + 1], scale, radius = 0.0f;
+        int border = 0;
+        std::string err;
+        if (setupFilter(type, d.rfilterP0, d.rfilterP1, lut, scale, radius, border, err)) {
+            j.num("rfilterRadius", radius);
+            j.num("rfilterBorder", border);
+        }
+        if (type == HPT_FILTER_BOX) j.num("rfilterBoxRadius", d.rfilterP0 < 0 ? 0.5f : d.rfilterP0);
+        if (type == HPT_FILTER_GAUSSIAN) j.num("rfilterStddev", d.rfilterP0 < 0 ? 0.5f : d.rfilterP0);
+        if (type == HPT_FILTER_MITCHELL) {
+            j.num("rfilterB", d.rfilterP0 < 0 ? 1.0f / 3.0f : d.rfilterP0);
+            j.num("rfilterC", d.rfilterP1 < 0 ? 1.0f / 3.0f : d.rfilterP1);
+        }
+        if (type == HPT_FILTER_LANCZOS) j.num("rfilterLobes", d.rfilterP0 < 0 ? 3 : (int) d.rfilterP0);
+    }
     j.close('}');
     j.open("bsdfs", '[');
     for (const BsdfDesc &b : d.bsdfs) bsdfJSON(j, b);

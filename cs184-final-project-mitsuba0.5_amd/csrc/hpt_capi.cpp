@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/hairpt.h"
+#include "../../include/hairpt_test.h"
 #include "host/host_scene.h"
 #include "hpt_device.h"
 #include "kernels/hpt_kernels.h"
@@ -123,8 +124,11 @@ struct hpt_context {
     uint32_t *qTrace = nullptr, *qShadow = nullptr, *qShade[2] = {nullptr, nullptr};
     uint32_t *counters = nullptr;
     uint64_t *dstats = nullptr;
-    float4 *partial = nullptr;     /* film splat partials: slots x 9 (k_splat -> k_gather) */
-    uint64_t partialSlots = 0;
+    float4 *partial = nullptr;     /* film splat partials: slots x (2 border + 1)^2 (k_splat -> k_gather) */
+    uint64_t partialCap = 0;       /* float4s allocated */
+    /* the last hpt_render's samples are still in P.pos / P.li, in its shard's slot order, when it
+       was one wave of this many samples per pixel (hpt_get_render_samples); 0: not available */
+    uint32_t samplesSpp = 0;
     /* block ownership of the last render call's shard (blockOf / localOf of HptWave) */
     uint32_t *dBlockOf = nullptr;
     int32_t *dLocalOf = nullptr;
@@ -279,6 +283,35 @@ int checkFault(hpt_context *c) {
         return setErr(c, HPT_ETRAVERSAL, "kd-tree traversal exceeded 2^18 leaf rounds for a ray (malformed tree?)");
     if (f & HPT_FAULT_RESTARTS)
         return setErr(c, HPT_ETRAVERSAL, "kd-tree traversal exceeded its kd-restart bound for a ray");
+    return HPT_OK;
+}
+
+/* the film splat's scratch: (2 border + 1)^2 partial sums per owned pixel slot */
+int ensurePartial(hpt_context *c, uint64_t slots) {
+    const uint64_t n = 2 * (uint64_t) c->sc.filterBorder + 1, need = slots * n * n;
+    if (need <= c->partialCap) return HPT_OK;
+    if (c->partial) (void) hipFree(c->partial);
+    c->partial = nullptr;
+    c->partialCap = 0;
+    HIPCHK(c, hipMalloc((void **) &c->partial, need * sizeof(float4)));
+    c->partialCap = need;
+    return HPT_OK;
+}
+
+/* samples of every pixel per wave: the whole range, or as many as max_wave_paths (0 = automatic,
+   HBM-sized waves) leaves room for over the shard's pixel slots */
+uint32_t waveSpp(uint64_t slots, uint64_t sppCount, uint64_t maxWavePaths) {
+    const uint64_t maxWave = maxWavePaths ? maxWavePaths : (uint64_t) 1 << 26;
+    return (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>(sppCount, maxWave / slots));
+}
+
+/* the film filter of c->desc into the kernels' scene record (setupFilter) */
+int configureFilter(hpt_context *c) {
+    std::string err;
+    const SceneDesc &d = c->desc;
+    if (!setupFilter(filterTypeOf(d.rfilter), d.rfilterP0, d.rfilterP1, c->sc.filter, c->sc.filterScale,
+                     c->sc.filterRadius, c->sc.filterBorder, err))
+        return setErr(c, HPT_EINVAL, err);
     return HPT_OK;
 }
 
@@ -653,6 +686,42 @@ int hpt_set_sunsky(hpt_context *c, const float sun_direction[3], float turbidity
     return HPT_OK;
 }
 
+static_assert(HPT_RFILTER_BOX == HPT_FILTER_BOX && HPT_RFILTER_TENT == HPT_FILTER_TENT &&
+                  HPT_RFILTER_GAUSSIAN == HPT_FILTER_GAUSSIAN && HPT_RFILTER_MITCHELL == HPT_FILTER_MITCHELL &&
+                  HPT_RFILTER_CATMULLROM == HPT_FILTER_CATMULLROM && HPT_RFILTER_LANCZOS == HPT_FILTER_LANCZOS,
+              "hairpt.h numbers the filters like the host code");
+
+int hpt_set_rfilter(hpt_context *c, int type, float p0, float p1) {
+    if (!c) return HPT_EINVAL;
+    float lut[HPT_FILTER_RES + 1], scale, radius;
+    int border;
+    std::string err;
+    if (!setupFilter(type, p0, p1, lut, scale, radius, border, err)) return setErr(c, HPT_EINVAL, err);
+    c->desc.rfilter = kFilterNames[type];
+    c->desc.rfilterP0 = p0;
+    c->desc.rfilterP1 = p1;
+    /* the film filter is no part of what hpt_prepare builds (kd-tree, tables): a prepared
+       context takes it at once; the next render uploads the changed scene record */
+    if (c->prepared) return configureFilter(c);
+    return HPT_OK;
+}
+
+int hpt_get_rfilter(hpt_context *c, int *type, float *radius, int *border, float lut[32], float *scale) {
+    if (!c) return HPT_EINVAL;
+    float l[HPT_FILTER_RES + 1], s, r;
+    int b;
+    std::string err;
+    const int t = filterTypeOf(c->desc.rfilter);
+    if (!setupFilter(t, c->desc.rfilterP0, c->desc.rfilterP1, l, s, r, b, err)) return setErr(c, HPT_EINVAL, err);
+    static_assert(HPT_FILTER_RES + 1 == 32, "hairpt.h documents a 32-entry LUT");
+    if (type) *type = t;
+    if (radius) *radius = r;
+    if (border) *border = b;
+    if (lut) std::memcpy(lut, l, sizeof(l));
+    if (scale) *scale = s;
+    return HPT_OK;
+}
+
 static int uploadScene(hpt_context *c);
 
 int hpt_prepare(hpt_context *c) {
@@ -956,7 +1025,8 @@ static int uploadScene(hpt_context *c) {
         r |= upload(c, zero, sizeof(zero), (const void **) &sc.fault);
     }
     if (r) return HPT_EDEVICE;
-    setupTent(sc.tent, sc.tentScale);
+    if (int rf = configureFilter(c)) return rf;
+    c->samplesSpp = 0;
     sc.maxDepth = d.maxDepth;
     sc.rrDepth = d.rrDepth;
     sc.strictNormals = d.strictNormals ? 1 : 0;
@@ -1171,21 +1241,15 @@ static int renderImpl(hpt_context *c, const hpt_render_params *prm, float4 *dFil
     const int sppBegin = prm->spp_begin, sppEnd = prm->spp_end;
     if (sppEnd < sppBegin || sppBegin < 0) return setErr(c, HPT_EINVAL, "bad spp range");
     std::memset(&c->stats, 0, sizeof(c->stats));
+    c->samplesSpp = 0;
     if (slots == 0 || sppEnd == sppBegin) return HPT_OK;
-    uint64_t maxWave = prm->max_wave_paths ? prm->max_wave_paths : (uint64_t) 1 << 26;
-    uint32_t nSpp = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>(sppEnd - sppBegin, maxWave / slots));
+    uint32_t nSpp = waveSpp(slots, (uint64_t) (sppEnd - sppBegin), prm->max_wave_paths);
     const uint64_t waveCap = slots * nSpp;
     if (waveCap > 0xffffffffull) return setErr(c, HPT_EINVAL, "wave too large");
     int r = ensureWave(c, waveCap);
     if (r) return r;
     const uint32_t tailPaths = c->tailPaths;
-    if (slots > c->partialSlots) {
-        if (c->partial) (void) hipFree(c->partial);
-        c->partial = nullptr;
-        c->partialSlots = 0;
-        HIPCHK(c, hipMalloc((void **) &c->partial, slots * 9 * sizeof(float4)));
-        c->partialSlots = slots;
-    }
+    if (int rp = ensurePartial(c, slots)) return rp;
     hipStream_t s = c->stream;
     c->P.blockCost = c->dBlockCost;
     c->P.costStride = (uint32_t) c->ownCap;
@@ -1516,6 +1580,7 @@ static int renderImpl(hpt_context *c, const hpt_render_params *prm, float4 *dFil
         c->stats.prim_slots = hs[7];
         c->stats.binary_nodes = hs[21];
     }
+    if (c->stats.waves == 1) c->samplesSpp = (uint32_t) (sppEnd - sppBegin); /* P.pos / P.li hold the frame */
     c->stats.bounces = bounces;
     c->stats.max_bounces = maxB;
     c->stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1542,6 +1607,111 @@ int hpt_render(hpt_context *c, const hpt_render_params *prm, float *film) {
     (void) hipFree(d);
     if (r) return r;
     if (e != hipSuccess) return setErr(c, HPT_EDEVICE, hipGetErrorString(e));
+    return HPT_OK;
+}
+
+/* the image pixel (y * W + x) of pixel slot `slot` of the current ownership tables, -1 when the
+   slot lies outside the frame (the last blocks of a frame that is no multiple of 32) */
+static int64_t slotPixel(const hpt_context *c, uint64_t slot, int W, int H, int nbx) {
+    const uint32_t b = c->ownBlocks[(size_t) (slot >> 10)], inner = (uint32_t) (slot & 1023u);
+    const int px = (int) (b % (uint32_t) nbx) * HPT_BLOCK + (int) (inner & 31u);
+    const int py = (int) (b / (uint32_t) nbx) * HPT_BLOCK + (int) (inner >> 5);
+    return px < W && py < H ? (int64_t) py * W + px : -1;
+}
+
+int hpt_film_splat_batch(hpt_context *c, int n_spp, const float *pos, const float *rgb, int shard, int n_shards,
+                         uint64_t max_wave_paths, float *film) {
+    if (!c || !pos || !rgb || !film || n_spp <= 0) return setErr(c, HPT_EINVAL, "hpt_film_splat_batch: bad arguments");
+    if (c->device == HPT_HOST_ONLY) return setErr(c, HPT_EDEVICE, "host-only context cannot render");
+    if (!c->prepared) return setErr(c, HPT_ESTATE, "hpt_prepare() must succeed before hpt_film_splat_batch");
+    HIPCHK(c, hipSetDevice(c->device));
+    const HptScene &sc = c->sc;
+    const int W = sc.cam.width, H = sc.cam.height;
+    const int nbx = (W + HPT_BLOCK - 1) / HPT_BLOCK, nby = (H + HPT_BLOCK - 1) / HPT_BLOCK;
+    const int nShards = std::max(1, n_shards);
+    if (shard < 0 || shard >= nShards) return setErr(c, HPT_EINVAL, "bad shard");
+    if (int r0 = ensureOwnership(c, W, H, nbx, nby, shard, nShards)) return r0;
+    c->samplesSpp = 0; /* the wave buffers are about to hold the caller's samples */
+    const uint64_t slots = (uint64_t) c->ownLocal * 1024u;
+    if (slots == 0) return HPT_OK;
+    /* the waves of an hpt_render of n_spp samples per pixel */
+    const uint32_t nSpp = waveSpp(slots, (uint64_t) n_spp, max_wave_paths);
+    const uint64_t waveCap = slots * nSpp;
+    if (waveCap > 0xffffffffull) return setErr(c, HPT_EINVAL, "wave too large");
+    if (int r = ensureWave(c, waveCap)) return r;
+    if (int r = ensurePartial(c, slots)) return r;
+    hipStream_t s = c->stream;
+    const size_t pixels = (size_t) W * H;
+    float4 *dFilm = nullptr;
+    HIPCHK(c, hipMalloc((void **) &dFilm, pixels * 16));
+    hipError_t e = hipMemcpy(dFilm, film, pixels * 16, hipMemcpyHostToDevice);
+    std::vector<float> hp((size_t) waveCap * 2), hl((size_t) waveCap * 4);
+    for (int j0 = 0; j0 < n_spp && e == hipSuccess; j0 += (int) nSpp) {
+        HptWave w;
+        w.sppBegin = (uint32_t) j0;
+        w.nSpp = (uint32_t) std::min<int>((int) nSpp, n_spp - j0);
+        w.nPaths = (uint32_t) (slots * w.nSpp);
+        w.width = W;
+        w.height = H;
+        w.nbx = nbx;
+        w.shard = shard;
+        w.nShards = nShards;
+        w.blockOf = c->dBlockOf;
+        w.localOf = c->dLocalOf;
+        w.doneIf = nullptr;
+        w.doneParity = 0;
+        /* pixel-major image order -> the wave's path ids (slot * nSpp + sample) */
+        for (uint64_t slot = 0; slot < slots; ++slot) {
+            const int64_t pix = slotPixel(c, slot, W, H, nbx);
+            for (uint32_t jj = 0; jj < w.nSpp; ++jj) {
+                const size_t id = (size_t) (slot * w.nSpp + jj);
+                if (pix < 0) { /* k_splat never reads these */
+                    hp[2 * id] = hp[2 * id + 1] = 0.0f;
+                    hl[4 * id] = -1.0f, hl[4 * id + 1] = hl[4 * id + 2] = hl[4 * id + 3] = 0.0f;
+                    continue;
+                }
+                const size_t src = (size_t) pix * (size_t) n_spp + (size_t) j0 + jj;
+                hp[2 * id] = pos[2 * src], hp[2 * id + 1] = pos[2 * src + 1];
+                hl[4 * id] = rgb[3 * src], hl[4 * id + 1] = rgb[3 * src + 1], hl[4 * id + 2] = rgb[3 * src + 2];
+                hl[4 * id + 3] = 0.0f;
+            }
+        }
+        e = hipMemcpyAsync(c->P.pos, hp.data(), (size_t) w.nPaths * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->P.li, hl.data(), (size_t) w.nPaths * 16, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hpt_launch_gather(sc, w, c->P, c->partial, dFilm, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s); /* hp / hl are filled again for the next wave */
+    }
+    if (e == hipSuccess) e = hipMemcpy(film, dFilm, pixels * 16, hipMemcpyDeviceToHost);
+    (void) hipFree(dFilm);
+    if (e != hipSuccess) return setErr(c, HPT_EDEVICE, std::string("hpt_film_splat_batch: ") + hipGetErrorString(e));
+    return HPT_OK;
+}
+
+int hpt_get_render_samples(hpt_context *c, float *pos, float *rgb, uint64_t *n) {
+    if (!c) return HPT_EINVAL;
+    if (c->device == HPT_HOST_ONLY) return setErr(c, HPT_EDEVICE, "host-only context cannot render");
+    if (!c->prepared || c->samplesSpp == 0)
+        return setErr(c, HPT_ESTATE, "hpt_get_render_samples: the last hpt_render was not a single wave of paths "
+                                     "(or nothing was rendered since hpt_prepare / hpt_film_splat_batch)");
+    const int W = c->sc.cam.width, H = c->sc.cam.height, nbx = (W + HPT_BLOCK - 1) / HPT_BLOCK;
+    const uint32_t spp = c->samplesSpp;
+    if (n) *n = (uint64_t) W * H * spp;
+    if (!pos && !rgb) return HPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t slots = (uint64_t) c->ownLocal * 1024u, paths = slots * spp;
+    std::vector<float> hp((size_t) paths * 2), hl((size_t) paths * 4);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(hp.data(), c->P.pos, (size_t) paths * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hl.data(), c->P.li, (size_t) paths * 16, hipMemcpyDeviceToHost));
+    for (uint64_t slot = 0; slot < slots; ++slot) {
+        const int64_t pix = slotPixel(c, slot, W, H, nbx);
+        if (pix < 0) continue;
+        for (uint32_t jj = 0; jj < spp; ++jj) {
+            const size_t id = (size_t) (slot * spp + jj), dst = (size_t) pix * spp + jj;
+            if (pos) pos[2 * dst] = hp[2 * id], pos[2 * dst + 1] = hp[2 * id + 1];
+            if (rgb) rgb[3 * dst] = hl[4 * id], rgb[3 * dst + 1] = hl[4 * id + 1], rgb[3 * dst + 2] = hl[4 * id + 2];
+        }
+    }
     return HPT_OK;
 }
 
@@ -1609,6 +1779,10 @@ int hpt_render_multi(hpt_context *const *ctxs, int n, const hpt_render_params *p
             c->sc.hideEmitters != c0->sc.hideEmitters || c->sc.scramble != c0->sc.scramble || c->desc.spp != c0->desc.spp)
             return setErr(c0, HPT_EINVAL, "hpt_render_multi: context " + std::to_string(g) +
                                               " has a different camera, sampler or integrator setting");
+        if (std::memcmp(c->sc.filter, c0->sc.filter, sizeof(c->sc.filter)) != 0 || c->sc.filterScale != c0->sc.filterScale ||
+            c->sc.filterRadius != c0->sc.filterRadius || c->sc.filterBorder != c0->sc.filterBorder)
+            return setErr(c0, HPT_EINVAL, "hpt_render_multi: context " + std::to_string(g) +
+                                              " has a different reconstruction filter (hpt_set_rfilter on every context)");
         if (c->blockWeights != c0->blockWeights)
             return setErr(c0, HPT_EINVAL, "hpt_render_multi: context " + std::to_string(g) +
                                               " deals the blocks with different weights (hpt_set_block_weights on every context)");

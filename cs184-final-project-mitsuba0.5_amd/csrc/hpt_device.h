@@ -19,6 +19,7 @@ struct __attribute__((aligned(16))) HptF4 {
 #define HPT_SOBOL_BITS 52      /* sobolseq.h:34 */
 #define HPT_BLOCK 32           /* mitsuba.cpp:144 block size */
 #define HPT_FILTER_RES 31      /* rfilter.h:28 MTS_FILTER_RESOLUTION */
+#define HPT_MAX_FILTER_BORDER 3 /* largest rfilter.cpp:50 border with a k_splat / k_gather instantiation (lanczos-3) */
 
 /* BSDF type flags (render/bsdf.h:224-285) */
 #define HPT_ENULL 0x00001u
@@ -230,8 +231,12 @@ struct HptScene {
     uint32_t scramble;          /* low 32 bits of sampleTEA(scramble) (sobol.cpp:92-102), 0 = off */
     const uint64_t *vdc;        /* rows x 52 */
     const uint64_t *vdcInv;     /* rows x 52 */
-    float tent[HPT_FILTER_RES + 1];
-    float tentScale;
+    /* the film's reconstruction filter as ReconstructionFilter::configure leaves it
+       (rfilter.cpp:37-55; setupFilter): m_values, m_scaleFactor, m_radius, m_borderSize */
+    float filter[HPT_FILTER_RES + 1];
+    float filterScale;
+    float filterRadius;
+    int filterBorder;           /* 1..HPT_MAX_FILTER_BORDER: which k_splat / k_gather instantiation runs */
     int maxDepth, rrDepth, strictNormals, hideEmitters;
     uint32_t *fault;            /* device word: HPT_FAULT_* bits set by the traversal bounds */
     uint32_t maxLeafRounds;     /* traversal bounds of one ray (HPT_MAX_LEAF_ROUNDS / HPT_MAX_RESTARTS unless */

@@ -157,7 +157,8 @@ hipError_t hpt_launch_tail(const HptScene &sc, const HptPaths &P, const uint32_t
                            uint32_t *counters, uint64_t items, uint32_t tailFrom, hipStream_t s);
 /* dst[i] += src[i] over n RGBW pixels (hpt_render_multi's film combine) */
 hipError_t hpt_launch_film_add(float4 *dst, const float4 *src, size_t n, hipStream_t s);
-/* k_splat + k_gather; partial = (nPaths / nSpp) * 9 float4 of scratch */
+/* k_splat + k_gather of the film filter's border B = sc.filterBorder (1..3; any other value is
+   hipErrorInvalidValue); partial = (nPaths / nSpp) * (2B+1)^2 float4 of scratch */
 hipError_t hpt_launch_gather(const HptScene &sc, const HptWave &w, const HptPaths &P, float4 *partial, float4 *film,
                              hipStream_t s);
 /* triangle-mesh scenes (C1, hpt_mesh.h): every camera sample of the wave to termination, one lane

@@ -16,7 +16,7 @@
  *                 continuation ray per path
  *   k_post        env hit + MIS (:236-264), throughput, Russian roulette
  *                 (:270-286); survivors re-enter the shade queue
- *   k_splat/k_gather  deterministic tent-filter accumulation of all samples
+ *   k_splat/k_gather  deterministic reconstruction-filter accumulation of all samples
  *                 into an RGBW film (imageblock.h:124-204)
  *
  * Queues are compacted with a wave64 ballot + one atomic per wave.  A
@@ -3321,14 +3321,25 @@ k_tail_multi(HptScene sc, HptPaths P, HptTail T, uint32_t *__restrict__ counters
 /* Deterministic film accumulation (imageblock.h:124-204 + renderproc.cpp:
    142-145) in two passes.  Weights use the sample's block-relative
    coordinates exactly like ImageBlock::put, and invalid samples (non-finite
-   or negative, imageblock.h:147-151) are skipped.
+   or negative, imageblock.h:147-151) are skipped.  B is the filter's border
+   (rfilter.cpp:50: 1 box / tent, 2 gaussian / mitchell / catmullrom, 3 lanczos):
+   a sample in pixel p touches ceil(p+f-0.5-r) .. floor(p+f-0.5+r), inside p +- B,
+   and the block's origin is block - B as in ImageBlock (imageblock.h:158-160).
 
-   k_splat: one wave per owned pixel slot; its lanes read the slot's samples
-   (consecutive path ids: coalesced) and accumulate the tent-weighted
-   contribution to each of the 3x3 neighbour pixels, reduced across the wave
-   with a fixed xor tree -> partial[slot][9] (RGB, weight). */
-extern "C" __global__ __launch_bounds__(256) void k_splat(HptScene sc, HptWave w, HptPaths P,
-                                                           float4 *__restrict__ partial) {
+   splatSlot: one wave per owned pixel slot; its lanes read the slot's samples
+   (consecutive path ids: coalesced) and accumulate the filter-weighted
+   contribution to each of the (2B+1)^2 neighbour pixels, reduced across the wave
+   with a fixed xor tree -> partial[slot][(2B+1)^2] (RGB, weight).  ROWS footprint
+   rows are accumulated per pass over the slot's samples: all three at once for
+   B = 1 (36 accumulators), one row per pass for B = 2, 3 (20 / 28 accumulators;
+   49 x 4 would not fit the register file at a useful occupancy) -- the later
+   passes re-read the slot's samples (nSpp x 24 bytes, L1/L2 hits).  A pixel's sum
+   has the same order in every shape: lane-local in sample order, then the tree. */
+template <int B, int ROWS>
+__device__ __forceinline__ void splatSlot(const HptScene &sc, const HptWave &w, const HptPaths &P,
+                                          float4 *__restrict__ partial) {
+    constexpr int N = 2 * B + 1;
+    static_assert(N % ROWS == 0, "the passes cover the footprint's rows exactly");
     if (w.doneIf && !hptWaveDone(w.doneIf, w.doneParity)) return; /* uniform: the host gathers later */
     const uint32_t slot = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63u;
@@ -3339,85 +3350,103 @@ extern "C" __global__ __launch_bounds__(256) void k_splat(HptScene sc, HptWave w
     const int bx = (int) (b % w.nbx), by = (int) (b / w.nbx);
     const int px = bx * HPT_BLOCK + (int) (inner & 31u), py = by * HPT_BLOCK + (int) (inner >> 5);
     if (px >= w.width || py >= w.height) return; /* wave-uniform: never read back */
-    const float ox = (float) (bx * HPT_BLOCK - 1), oy = (float) (by * HPT_BLOCK - 1);
-    float acc[9][4];
+    const float ox = (float) (bx * HPT_BLOCK - B), oy = (float) (by * HPT_BLOCK - B);
+    const float radius = sc.filterRadius;
+    for (int r0 = -B; r0 <= B; r0 += ROWS) { /* one trip when ROWS == N */
+        float acc[ROWS * N][4];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.0f;
-    /* the lane's samples lane, lane + 64, ... in that order (the film's summation order); their
-       records are loaded four at a time ahead of the accumulation, so a wave waits on one round
-       trip per four samples instead of one per sample */
-    for (uint32_t j0 = lane; j0 < w.nSpp; j0 += 4 * 64) {
-        float4 lk[4];
-        float2 pk[4];
+        for (int k = 0; k < ROWS * N; ++k) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.0f;
+        /* the lane's samples lane, lane + 64, ... in that order (the film's summation order); their
+           records are loaded four at a time ahead of the accumulation, so a wave waits on one round
+           trip per four samples instead of one per sample */
+        for (uint32_t j0 = lane; j0 < w.nSpp; j0 += 4 * 64) {
+            float4 lk[4];
+            float2 pk[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t jj = j0 + 64u * k;
-            lk[k] = make_float4(-1.0f, 0.0f, 0.0f, 0.0f); /* past the wave's samples: rejected below */
-            pk[k] = make_float2(0.0f, 0.0f);
-            if (jj < w.nSpp) {
-                lk[k] = P.li[slot * w.nSpp + jj];
-                pk[k] = P.pos[slot * w.nSpp + jj];
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t jj = j0 + 64u * k;
+                lk[k] = make_float4(-1.0f, 0.0f, 0.0f, 0.0f); /* past the wave's samples: rejected below */
+                pk[k] = make_float2(0.0f, 0.0f);
+                if (jj < w.nSpp) {
+                    lk[k] = P.li[slot * w.nSpp + jj];
+                    pk[k] = P.pos[slot * w.nSpp + jj];
+                }
             }
-        }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 l = lk[k];
-            if (!(isfinite(l.x) && isfinite(l.y) && isfinite(l.z)) || l.x < 0 || l.y < 0 || l.z < 0) continue;
-            const float2 ps = pk[k];
-            const float rx = ps.x - 0.5f - ox, ry = ps.y - 0.5f - oy;
-            const float x0 = ceilf(rx - 1.0f), x1 = floorf(rx + 1.0f), y0 = ceilf(ry - 1.0f), y1 = floorf(ry + 1.0f);
+            for (int k = 0; k < 4; ++k) {
+                const float4 l = lk[k];
+                if (!(isfinite(l.x) && isfinite(l.y) && isfinite(l.z)) || l.x < 0 || l.y < 0 || l.z < 0) continue;
+                const float2 ps = pk[k];
+                const float rx = ps.x - 0.5f - ox, ry = ps.y - 0.5f - oy;
+                const float x0 = ceilf(rx - radius), x1 = floorf(rx + radius), y0 = ceilf(ry - radius),
+                            y1 = floorf(ry + radius);
 #pragma unroll
-            for (int dy = -1; dy <= 1; ++dy) {
-                const float yr = (float) (py + dy) - oy;
-                if (yr < y0 || yr > y1) continue;
-                const float wy = sc.tent[imin((int) fabsf((yr - ry) * sc.tentScale), HPT_FILTER_RES)];
+                for (int r = 0; r < ROWS; ++r) {
+                    const float yr = (float) (py + r0 + r) - oy;
+                    if (yr < y0 || yr > y1) continue;
+                    const float wy = sc.filter[imin((int) fabsf((yr - ry) * sc.filterScale), HPT_FILTER_RES)];
 #pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const float xr = (float) (px + dx) - ox;
-                    if (xr < x0 || xr > x1) continue;
-                    const float wx = sc.tent[imin((int) fabsf((xr - rx) * sc.tentScale), HPT_FILTER_RES)];
-                    const float wgt = wx * wy;
-                    float *a = acc[(dy + 1) * 3 + (dx + 1)];
-                    a[0] += wgt * l.x;
-                    a[1] += wgt * l.y;
-                    a[2] += wgt * l.z;
-                    a[3] += wgt * 1.0f;
+                    for (int dx = -B; dx <= B; ++dx) {
+                        const float xr = (float) (px + dx) - ox;
+                        if (xr < x0 || xr > x1) continue;
+                        const float wx = sc.filter[imin((int) fabsf((xr - rx) * sc.filterScale), HPT_FILTER_RES)];
+                        const float wgt = wx * wy;
+                        float *a = acc[r * N + (dx + B)];
+                        a[0] += wgt * l.x;
+                        a[1] += wgt * l.y;
+                        a[2] += wgt * l.z;
+                        a[3] += wgt * 1.0f;
+                    }
                 }
             }
         }
-    }
 #pragma unroll
-    for (int k = 0; k < 9; ++k)
+        for (int k = 0; k < ROWS * N; ++k)
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+            for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) acc[k][c] += __shfl_xor(acc[k][c], off);
-    if (lane == 0) {
+                for (int off = 32; off > 0; off >>= 1) acc[k][c] += __shfl_xor(acc[k][c], off);
+        if (lane == 0) {
+            float4 *row = partial + (size_t) slot * (N * N) + (r0 + B) * N;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) partial[(size_t) slot * 9 + k] = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+            for (int k = 0; k < ROWS * N; ++k) row[k] = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+        }
     }
 }
+extern "C" __global__ __launch_bounds__(256) void k_splat(HptScene sc, HptWave w, HptPaths P,
+                                                           float4 *__restrict__ partial) {
+    splatSlot<1, 3>(sc, w, P, partial);
+}
+extern "C" __global__ __launch_bounds__(256) void k_splat_b2(HptScene sc, HptWave w, HptPaths P,
+                                                              float4 *__restrict__ partial) {
+    splatSlot<2, 1>(sc, w, P, partial);
+}
+extern "C" __global__ __launch_bounds__(256) void k_splat_b3(HptScene sc, HptWave w, HptPaths P,
+                                                              float4 *__restrict__ partial) {
+    splatSlot<3, 1>(sc, w, P, partial);
+}
 
-/* k_gather: every pixel adds, in a fixed neighbour order, the partial sums
-   its 3x3 neighbours (owned by this shard) addressed to it. */
-extern "C" __global__ __launch_bounds__(256) void k_gather(HptScene sc, HptWave w, const float4 *__restrict__ partial,
-                                                            float4 *film) {
+/* gatherPixel: every pixel adds, in a fixed neighbour order (rows, then columns), the
+   partial sums its (2B+1)^2 neighbours (owned by this shard) addressed to it. */
+template <int B>
+__device__ __forceinline__ void gatherPixel(const HptWave &w, const float4 *__restrict__ partial, float4 *film) {
+    constexpr int N = 2 * B + 1;
     if (w.doneIf && !hptWaveDone(w.doneIf, w.doneParity)) return; /* uniform: the host gathers later */
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= (uint32_t) (w.width * w.height)) return;
     const int x = (int) (pix % (uint32_t) w.width), y = (int) (pix / (uint32_t) w.width);
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     bool any = false;
-    for (int qy = y - 1; qy <= y + 1; ++qy) {
+    for (int qy = y - B; qy <= y + B; ++qy) {
         if (qy < 0 || qy >= w.height) continue;
-        for (int qx = x - 1; qx <= x + 1; ++qx) {
+        for (int qx = x - B; qx <= x + B; ++qx) {
             if (qx < 0 || qx >= w.width) continue;
             const int bx = qx / HPT_BLOCK, by = qy / HPT_BLOCK;
             const uint32_t b = (uint32_t) (by * w.nbx + bx);
             const int32_t lb = w.localOf[b];
             if (lb < 0) continue; /* another shard's block */
             const uint32_t slot = ((uint32_t) lb << 10) | ((uint32_t) (qy & 31) << 5) | (uint32_t) (qx & 31);
-            const float4 p = partial[(size_t) slot * 9 + (y - qy + 1) * 3 + (x - qx + 1)];
+            const float4 p = partial[(size_t) slot * (N * N) + (y - qy + B) * N + (x - qx + B)];
             acc.x += p.x;
             acc.y += p.y;
             acc.z += p.z;
@@ -3429,6 +3458,18 @@ extern "C" __global__ __launch_bounds__(256) void k_gather(HptScene sc, HptWave 
         float4 f = film[pix];
         film[pix] = make_float4(f.x + acc.x, f.y + acc.y, f.z + acc.z, f.w + acc.w);
     }
+}
+extern "C" __global__ __launch_bounds__(256) void k_gather(HptScene sc, HptWave w, const float4 *__restrict__ partial,
+                                                            float4 *film) {
+    gatherPixel<1>(w, partial, film);
+}
+extern "C" __global__ __launch_bounds__(256) void k_gather_b2(HptScene sc, HptWave w,
+                                                               const float4 *__restrict__ partial, float4 *film) {
+    gatherPixel<2>(w, partial, film);
+}
+extern "C" __global__ __launch_bounds__(256) void k_gather_b3(HptScene sc, HptWave w,
+                                                               const float4 *__restrict__ partial, float4 *film) {
+    gatherPixel<3>(w, partial, film);
 }
 
 /* ------------------------------------------------------------------ */
@@ -3736,9 +3777,23 @@ hipError_t hpt_launch_film_add(float4 *dst, const float4 *src, size_t n, hipStre
 hipError_t hpt_launch_gather(const HptScene &sc, const HptWave &w, const HptPaths &P, float4 *partial, float4 *film,
                              hipStream_t s) {
     const uint64_t slots = w.nPaths / w.nSpp;
-    hipLaunchKernelGGL(k_splat, dim3(blocksFor(slots * 64, 256)), dim3(256), 0, s, sc, w, P, partial);
     const uint64_t n = (uint64_t) w.width * (uint64_t) w.height;
-    hipLaunchKernelGGL(k_gather, dim3(blocksFor(n, 256)), dim3(256), 0, s, sc, w, (const float4 *) partial, film);
+    const dim3 gs(blocksFor(slots * 64, 256)), gg(blocksFor(n, 256)), blk(256);
+    switch (sc.filterBorder) { /* the film filter's footprint (setupFilter admits borders 1..3) */
+    case 1:
+        hipLaunchKernelGGL(k_splat, gs, blk, 0, s, sc, w, P, partial);
+        hipLaunchKernelGGL(k_gather, gg, blk, 0, s, sc, w, (const float4 *) partial, film);
+        break;
+    case 2:
+        hipLaunchKernelGGL(k_splat_b2, gs, blk, 0, s, sc, w, P, partial);
+        hipLaunchKernelGGL(k_gather_b2, gg, blk, 0, s, sc, w, (const float4 *) partial, film);
+        break;
+    case 3:
+        hipLaunchKernelGGL(k_splat_b3, gs, blk, 0, s, sc, w, P, partial);
+        hipLaunchKernelGGL(k_gather_b3, gg, blk, 0, s, sc, w, (const float4 *) partial, film);
+        break;
+    default: return hipErrorInvalidValue; /* no kernel for this footprint: never a silent tent */
+    }
     return hipGetLastError();
 }
 hipError_t hpt_launch_sobol_batch(const HptScene &sc, int m, int n, const uint32_t *frame, const uint32_t *px,

@@ -97,6 +97,8 @@ SIGNATURES = {
     "hpt_set_bsdf_marschnerdielectric": (C.c_int, [C.c_void_p, C.c_float, C.c_float, _f, _f, _f]),
     "hpt_set_envmap_rgb": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_int, C.c_float, _f]),
     "hpt_set_sunsky": (C.c_int, [C.c_void_p, _f, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "hpt_set_rfilter": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "hpt_get_rfilter": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _f, C.POINTER(C.c_int), _f, _f]),
     "hpt_prepare": (C.c_int, [C.c_void_p]),
     "hpt_get_scene_info": (C.c_int, [C.c_void_p, C.POINTER(SceneInfo)]),
     "hpt_render": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), _f]),
@@ -123,6 +125,15 @@ SIGNATURES = {
     "hpt_env_batch": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _f, _f, _f, _f, _f, _f, _f]),
 }
 
+# the test hooks of include/hairpt_test.h
+TEST_SIGNATURES = {
+    "hpt_film_splat_batch": (C.c_int, [C.c_void_p, C.c_int, _f, _f, C.c_int, C.c_int, C.c_uint64, _f]),
+    "hpt_get_render_samples": (C.c_int, [C.c_void_p, _f, _f, _u64]),
+}
+
+# include/hairpt.h HPT_RFILTER_*, by the plugin's name
+RFILTERS = {"box": 0, "tent": 1, "gaussian": 2, "mitchell": 3, "catmullrom": 4, "lanczos": 5}
+
 _lib = None
 
 
@@ -137,7 +148,7 @@ def load_library(path: str = None):
             raise OSError("libhairpt.so not built at %s (run __graft_entry__.build())" % path)
         lib = C.CDLL(path)
         experiment = path != LIB_PATH
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **TEST_SIGNATURES}.items():
             if experiment and not hasattr(lib, name):
                 continue  # an older experiment build: exports added since then stay unbound
             fn = getattr(lib, name)
@@ -317,6 +328,27 @@ class Renderer:
         self._check(self.lib.hpt_set_sunsky(self.h, _p(d, _f), turbidity, sky_scale, sun_scale, sun_radius_scale,
                                             resolution))
 
+    def set_rfilter(self, kind, p0=-1.0, p1=-1.0):
+        """the film's reconstruction filter: a plugin name (or HPT_RFILTER_* number) and its
+        parameters (box: radius; gaussian: stddev; mitchell: B, C; lanczos: lobes), negative =
+        the plugin's default; before or after prepare()"""
+        if isinstance(kind, str):
+            if kind not in RFILTERS:
+                raise HairPTError("rfilter \"%s\" is not one of %s" % (kind, ", ".join(RFILTERS)), -1)
+            kind = RFILTERS[kind]
+        self._check(self.lib.hpt_set_rfilter(self.h, int(kind), p0, p1))
+
+    def rfilter(self) -> dict:
+        """the configured filter (hpt_get_rfilter): name, radius, border, the 32-entry LUT, its scale"""
+        t, b = C.c_int(), C.c_int()
+        radius, scale = C.c_float(), C.c_float()
+        lut = np.zeros(32, np.float32)
+        self._check(self.lib.hpt_get_rfilter(self.h, C.byref(t), C.byref(radius), C.byref(b), _p(lut, _f),
+                                             C.byref(scale)))
+        name = [k for k, v in RFILTERS.items() if v == t.value][0]
+        return {"type": name, "radius": np.float32(radius.value), "border": b.value, "lut": lut,
+                "scale": np.float32(scale.value)}
+
     def prepare(self):
         self._check(self.lib.hpt_prepare(self.h))
 
@@ -359,6 +391,31 @@ class Renderer:
         p = RenderParams(spp_begin, spp_end, 0, 1, max_wave_paths, int(collect_stats))
         r0._check(r0.lib.hpt_render_multi(hs, len(renderers), C.byref(p), _p(film, _f)))
         return film
+
+    def film_splat(self, pos, rgb, shard=0, n_shards=1, max_wave_paths=0, film=None) -> np.ndarray:
+        """test hook (hpt_film_splat_batch): the production k_splat + k_gather over the caller's
+        samples, pos (H, W, n_spp, 2) and rgb (H, W, n_spp, 3); accumulates into film"""
+        si = self.info()
+        pos = _f32(pos).reshape(si.height, si.width, -1, 2)
+        rgb = _f32(rgb).reshape(si.height, si.width, -1, 3)
+        assert pos.shape[2] == rgb.shape[2]
+        if film is None:
+            film = np.zeros((si.height, si.width, 4), dtype=np.float32)
+        self._check(self.lib.hpt_film_splat_batch(self.h, pos.shape[2], _p(pos, _f), _p(rgb, _f), shard, n_shards,
+                                                  max_wave_paths, _p(film, _f)))
+        return film
+
+    def render_samples(self):
+        """test hook (hpt_get_render_samples): (pos (H, W, spp, 2), rgb (H, W, spp, 3)) of the
+        last render, which must have been one wave"""
+        si = self.info()
+        n = C.c_uint64()
+        self._check(self.lib.hpt_get_render_samples(self.h, None, None, C.byref(n)))
+        spp = n.value // (si.width * si.height)
+        pos = np.zeros((si.height, si.width, spp, 2), np.float32)
+        rgb = np.zeros((si.height, si.width, spp, 3), np.float32)
+        self._check(self.lib.hpt_get_render_samples(self.h, _p(pos, _f), _p(rgb, _f), C.byref(n)))
+        return pos, rgb
 
     def stats(self) -> Stats:
         s = Stats()

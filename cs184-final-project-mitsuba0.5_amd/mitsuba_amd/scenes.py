@@ -148,7 +148,7 @@ XML = """<?xml version="1.0" encoding="utf-8"?>
       <string name="pixelFormat" value="rgb"/>
       <float name="gamma" value="2.2"/>
       <boolean name="banner" value="false"/>
-      <rfilter type="tent"/>
+      <rfilter type="{rfilter}"/>
     </film>
   </sensor>
 {bsdf}
@@ -206,8 +206,10 @@ def hair_files(name: str, workdir: str, n_strands: int | None = None):
     return out
 
 
-def make_scene(name: str, workdir: str, n_strands: int | None = None, **override) -> str:
-    """Write <workdir>/<name>_<n>.xml (+ hair files, cached) and return the XML path."""
+def make_scene(name: str, workdir: str, n_strands: int | None = None, rfilter: str = "tent", **override) -> str:
+    """Write <workdir>/<name>_<n>.xml (+ hair files, cached) and return the XML path.  rfilter is
+    the film's reconstruction filter plugin (box, tent, gaussian, mitchell, catmullrom, lanczos, or
+    a $variable for -D substitution); any other than the tent gets a file name of its own."""
     cfg = dict(CONFIGS[name])
     cfg.update(override)
     n = int(n_strands if n_strands is not None else cfg["n"])
@@ -220,8 +222,9 @@ def make_scene(name: str, workdir: str, n_strands: int | None = None, **override
     sx, sy, sz = cfg["sun"].split()
     xml = XML.format(name=name, spp=cfg["spp"], width=cfg["width"], height=cfg["height"],
                      max_depth=cfg["max_depth"], hairdefaults=defaults, cam=cfg["cam"],
-                     bsdf=cfg["bsdf"], shapes=shapes, sx=sx, sy=sy, sz=sz, **SUNSKY)
-    path = os.path.join(workdir, "%s_%d.xml" % (name, n))
+                     bsdf=cfg["bsdf"], shapes=shapes, sx=sx, sy=sy, sz=sz, rfilter=rfilter, **SUNSKY)
+    tag = "" if rfilter == "tent" else "_" + rfilter.lstrip("$")
+    path = os.path.join(workdir, "%s_%d%s.xml" % (name, n, tag))
     _write_atomic(path, xml)
     return path
 

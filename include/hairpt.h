@@ -59,7 +59,10 @@ int hpt_set_data_dir(hpt_context *ctx, const char *dir);
    shape "hair", bsdf "marschner"/"kajiyakay"/"roughplastic"/"marschnerdielectric"/"thindielectric"/"diffuse"
    (one per hair shape; several shapes per scene), emitter "sunsky"/"envmap"; or, for a
    triangle-mesh scene (C1, models/teapot), shape "obj"/"rectangle" with bsdf "diffuse" (constant
-   or "checkerboard" texture) / "plastic" / "twosided" over those two. */
+   or "checkerboard" texture) / "plastic" / "twosided" over those two.  The film's <rfilter> is
+   "box" / "tent" / "gaussian" / "mitchell" / "catmullrom" / "lanczos" with the plugin's
+   parameters (hpt_set_rfilter); a <film> without one gets the gaussian (src/librender/
+   film.cpp:90-94). */
 int hpt_load_scene_xml(hpt_context *ctx, const char *path, int n_defines, const char *const *keys,
                        const char *const *values);
 /* Process-wide -D defines, merged under the explicit ones by every later
@@ -143,6 +146,28 @@ int hpt_set_envmap_rgb(hpt_context *ctx, const float *rgb, int w, int h, float s
    sun rasterised into the envmap bitmap (sun_direction given explicitly) */
 int hpt_set_sunsky(hpt_context *ctx, const float sun_direction[3], float turbidity, float sky_scale,
                    float sun_scale, float sun_radius_scale, int resolution);
+
+/* The film's ReconstructionFilter (src/rfilters/{box,tent,gaussian,mitchell,catmullrom,
+   lanczos}.cpp constructors, configured by ReconstructionFilter::configure, src/libcore/
+   rfilter.cpp:37-55).  p0 / p1 are the plugin's parameters -- box: radius (box.cpp:38); gaussian:
+   stddev (gaussian.cpp:35-38); mitchell: B, C (mitchell.cpp:35-39); lanczos: lobes (lanczos.cpp:
+   35); tent and catmullrom have none -- and a negative value takes the plugin's default.  May be
+   called before or after hpt_prepare (the kd-tree is not rebuilt; the next render uses it).  A
+   scene described through the setters alone renders with the tent; hpt_load_scene_xml sets the
+   scene's filter.  The device film holds borders (rfilter.cpp:50, ceil(radius - 0.5)) of up to 3
+   pixels: a radius above 3.5 or not above 0 fails with HPT_EINVAL. */
+#define HPT_RFILTER_BOX 0
+#define HPT_RFILTER_TENT 1
+#define HPT_RFILTER_GAUSSIAN 2
+#define HPT_RFILTER_MITCHELL 3
+#define HPT_RFILTER_CATMULLROM 4
+#define HPT_RFILTER_LANCZOS 5
+int hpt_set_rfilter(hpt_context *ctx, int type, float p0, float p1);
+/* The configured filter, ReconstructionFilter's m_radius, m_borderSize, m_values[32] and
+   m_scaleFactor (include/mitsuba/core/rfilter.h:28-98; evalDiscretized, :76-77, reads
+   lut[min((int) |x * scale|, 31)]).  A border of 0 (radius <= 0.5) is reported, and run, as 1.
+   Any pointer may be NULL. */
+int hpt_get_rfilter(hpt_context *ctx, int *type, float *radius, int *border, float lut[32], float *scale);
 
 /* Build the hair kd-tree (HairKDTree ctor, hair.cpp:108-159), precompute the
    BSDF / envmap tables and upload the scene to HBM (Scene::preprocess).  A scene whose
