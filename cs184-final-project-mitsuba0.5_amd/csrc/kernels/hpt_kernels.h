@@ -41,6 +41,37 @@ static_assert(HPT_Q_COUNT <= HPT_CURSOR_OFFSET, "the counters precede the cursor
 #define HPT_CURSOR_SET(s) (HPT_CURSOR_OFFSET + (s) * HPT_CURSORS * HPT_CURSOR_STRIDE)
 #define HPT_COUNTER_WORDS (HPT_CURSOR_OFFSET + HPT_CURSOR_SETS * HPT_CURSORS * HPT_CURSOR_STRIDE)
 
+/* Traversal counter block (uint64 slots; the `stats` argument of the trace launches, hpt_stats
+   on the host).  The bounce traversal (tracePersistent) adds to the first twelve, the shadow
+   pair and HPT_TS_BIN_NODES, the camera packets (tracePackets) to the HPT_TS_PACKET_* slots. */
+enum HptTraversalStat {
+    HPT_TS_NODES = 0,          /* node visits (two-level HptNode4 fetches) */
+    HPT_TS_PRIMS,              /* primitive tests */
+    HPT_TS_CLOSEST_RAYS,
+    HPT_TS_SHADOW_RAYS,
+    HPT_TS_SHADOW_UNOCCLUDED,
+    HPT_TS_PRIM_EXACT,         /* segments that passed the fp32 pre-test */
+    HPT_TS_NODE_SLOTS,         /* SIMD lanes occupied by the node / primitive loops */
+    HPT_TS_PRIM_SLOTS,
+    HPT_TS_MAX_ROUNDS,         /* most leaf rounds / kd-restarts of one ray (atomicMax) */
+    HPT_TS_MAX_RESTARTS,
+    HPT_TS_RESTARTED_RAYS,
+    HPT_TS_RESTARTS,
+    HPT_TS_PACKET_NODES,       /* binary node visits of the packets (8-byte HptNode) */
+    HPT_TS_PACKET_PRIMS,
+    HPT_TS_PACKET_RAYS,
+    HPT_TS_PACKET_EXACT,
+    HPT_TS_PACKET_NODE_SLOTS,
+    HPT_TS_PACKET_PRIM_SLOTS,
+    HPT_TS_PACKET_FALLBACKS,   /* packets that fell back to one ray per lane */
+    HPT_TS_SHADOW_NODES,       /* node visits / primitive tests of shadow rays */
+    HPT_TS_SHADOW_PRIMS,
+    HPT_TS_BIN_NODES,          /* binary kd-node visits of the bounce traversal */
+    HPT_TS_COUNT = 24          /* slots allocated */
+};
+static_assert(HPT_TS_PACKET_NODES == 12 && HPT_TS_SHADOW_NODES == 19 && HPT_TS_BIN_NODES == 21,
+              "the traversal counter slots keep their numbers");
+
 /* One wave of paths: every pixel of this shard's 32x32 blocks x samples
    [sppBegin, sppBegin + nSpp).  Path id = slot * nSpp + (j - sppBegin),
    slot = (localBlock << 10) | (y%32 << 5) | (x%32). */

@@ -1038,25 +1038,25 @@ __device__ __forceinline__ void tracePersistent(const HptScene &sc, IO &io, uint
         }
         if (lane == 0) {
             unsigned long long *st = (unsigned long long *) stats;
-            atomicAdd(&st[0], (unsigned long long) tc.nodes);
-            atomicAdd(&st[1], (unsigned long long) tc.prims);
-            atomicAdd(&st[2], (unsigned long long) nC);
-            atomicAdd(&st[3], (unsigned long long) nS);
-            atomicAdd(&st[4], (unsigned long long) nU);
-            atomicAdd(&st[5], (unsigned long long) tc.exact);
-            atomicAdd(&st[6], (unsigned long long) tc.nodeSlots);
-            atomicAdd(&st[7], (unsigned long long) tc.primSlots);
-            /* [8]/[9] max rounds (leaves visited) / kd-restarts of one ray, [10] rays that
-               restarted, [11] restarts */
-            atomicMax(&st[8], (unsigned long long) maxRounds);
-            atomicMax(&st[9], (unsigned long long) maxRestarts);
-            atomicAdd(&st[10], (unsigned long long) restartRays);
-            atomicAdd(&st[11], (unsigned long long) restarts);
-            /* [19]/[20] node visits / primitive tests of shadow rays */
-            atomicAdd(&st[19], (unsigned long long) tc.shadowNodes);
-            atomicAdd(&st[20], (unsigned long long) tc.shadowPrims);
-            /* [21] binary kd-node visits (the byte model of SURVEY.md 8(d): 8 B per binary node) */
-            atomicAdd(&st[21], (unsigned long long) tc.binNodes);
+            atomicAdd(&st[HPT_TS_NODES], (unsigned long long) tc.nodes);
+            atomicAdd(&st[HPT_TS_PRIMS], (unsigned long long) tc.prims);
+            atomicAdd(&st[HPT_TS_CLOSEST_RAYS], (unsigned long long) nC);
+            atomicAdd(&st[HPT_TS_SHADOW_RAYS], (unsigned long long) nS);
+            atomicAdd(&st[HPT_TS_SHADOW_UNOCCLUDED], (unsigned long long) nU);
+            atomicAdd(&st[HPT_TS_PRIM_EXACT], (unsigned long long) tc.exact);
+            atomicAdd(&st[HPT_TS_NODE_SLOTS], (unsigned long long) tc.nodeSlots);
+            atomicAdd(&st[HPT_TS_PRIM_SLOTS], (unsigned long long) tc.primSlots);
+            /* max rounds (leaves visited) / kd-restarts of one ray, rays that restarted,
+               restarts */
+            atomicMax(&st[HPT_TS_MAX_ROUNDS], (unsigned long long) maxRounds);
+            atomicMax(&st[HPT_TS_MAX_RESTARTS], (unsigned long long) maxRestarts);
+            atomicAdd(&st[HPT_TS_RESTARTED_RAYS], (unsigned long long) restartRays);
+            atomicAdd(&st[HPT_TS_RESTARTS], (unsigned long long) restarts);
+            /* node visits / primitive tests of shadow rays */
+            atomicAdd(&st[HPT_TS_SHADOW_NODES], (unsigned long long) tc.shadowNodes);
+            atomicAdd(&st[HPT_TS_SHADOW_PRIMS], (unsigned long long) tc.shadowPrims);
+            /* binary kd-node visits (the byte model of SURVEY.md 8(d): 8 B per binary node) */
+            atomicAdd(&st[HPT_TS_BIN_NODES], (unsigned long long) tc.binNodes);
         }
     }
 }
@@ -1371,16 +1371,16 @@ __device__ __forceinline__ void tracePackets(const HptScene &sc, IO &io, uint32_
         }
         if (lane == 0) {
             unsigned long long *st = (unsigned long long *) stats;
-            /* the packet pass's own counters: [12] binary node visits (8-byte HptNode)
-               [13] primitive tests [14] rays [15] exact tests [16]/[17] node / primitive
-               SIMD slots [18] packets that fell back to one ray per lane */
-            atomicAdd(&st[12], (unsigned long long) tc.nodes);
-            atomicAdd(&st[13], (unsigned long long) tc.prims);
-            atomicAdd(&st[14], (unsigned long long) nC);
-            atomicAdd(&st[15], (unsigned long long) tc.exact);
-            atomicAdd(&st[16], (unsigned long long) tc.nodeSlots);
-            atomicAdd(&st[17], (unsigned long long) tc.primSlots);
-            atomicAdd(&st[18], (unsigned long long) fallbacks);
+            /* the packet pass's own counters: binary node visits (8-byte HptNode), primitive
+               tests, rays, exact tests, node / primitive SIMD slots, packets that fell back to
+               one ray per lane */
+            atomicAdd(&st[HPT_TS_PACKET_NODES], (unsigned long long) tc.nodes);
+            atomicAdd(&st[HPT_TS_PACKET_PRIMS], (unsigned long long) tc.prims);
+            atomicAdd(&st[HPT_TS_PACKET_RAYS], (unsigned long long) nC);
+            atomicAdd(&st[HPT_TS_PACKET_EXACT], (unsigned long long) tc.exact);
+            atomicAdd(&st[HPT_TS_PACKET_NODE_SLOTS], (unsigned long long) tc.nodeSlots);
+            atomicAdd(&st[HPT_TS_PACKET_PRIM_SLOTS], (unsigned long long) tc.primSlots);
+            atomicAdd(&st[HPT_TS_PACKET_FALLBACKS], (unsigned long long) fallbacks);
         }
     }
 }

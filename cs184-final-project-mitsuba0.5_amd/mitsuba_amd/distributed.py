@@ -3,7 +3,7 @@
 The frame's 32x32 blocks (the reference's block size, src/mitsuba/mitsuba.cpp:144)
 are dealt cyclically along a Hilbert curve over the block grid: rank r renders
 every sample of the blocks at positions r, r + world, r + 2 world, ... of that
-curve (block_owner below; hpt_capi.cpp blockOrder is the renderer's own copy).
+curve (block_owner below; hpt_render_driver.cpp blockOrder is the renderer's own copy).
 N consecutive blocks of the curve form a compact patch, so every rank gets one
 block of every patch and the hair's uneven screen coverage is spread evenly
 (SURVEY.md 8e's plain b % world deal hands whole block columns to a rank
@@ -53,7 +53,7 @@ def block_owner(nbx: int, nby: int, world: int) -> list[int]:
 
 
 def block_owner_weighted(nbx: int, nby: int, world: int, weights) -> list[int]:
-    """The work-balanced deal (hpt_capi.cpp dealBlocks, hpt_set_block_weights): blocks by
+    """The work-balanced deal (hpt_render_driver.cpp dealBlocks, hpt_set_block_weights): blocks by
     descending weight (ties in Hilbert order), each to the rank with the least weight so far
     (ties to the lowest rank).  weights[b] is block b's measured work."""
     order = block_order(nbx, nby)

@@ -193,7 +193,7 @@ int hpt_get_scene_info(hpt_context *ctx, hpt_scene_info *out);
 typedef struct hpt_render_params {
     int spp_begin, spp_end;        /* render samples [spp_begin, spp_end) of every pixel */
     int shard, n_shards;           /* the 32x32 blocks at positions shard, shard + n_shards, ... of a
-                                      Hilbert curve over the block grid (multi-GPU; hpt_capi.cpp blockOrder) */
+                                      Hilbert curve over the block grid (multi-GPU; hpt_render_driver.cpp blockOrder) */
     uint64_t max_wave_paths;       /* 0 = automatic (HBM-sized waves) */
     int collect_stats;             /* 0 none, 1 per-kernel HIP event timing,
                                       2 timing + traversal counters (slower k_trace variant),

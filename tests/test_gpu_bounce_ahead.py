@@ -1,4 +1,4 @@
-"""GPU tests of device-side bounce control (hpt_capi.cpp renderImpl).
+"""GPU tests of device-side bounce control (hpt_render_driver.cpp renderHairWave).
 
 A wave of paths rendered again (same spp range and shard since the last
 prepare) launches its bounces ahead on the schedule recorded the first time:
@@ -22,14 +22,14 @@ pytestmark = pytest.mark.gpu
 HAIRCURL_RADII = (0.0025, 0.0025)
 
 
-def _render_twice(name, n, radii, monkeypatch, ahead, hook, tail, max_wave=0, times=2):
+def _render_twice(name, n, radii, monkeypatch, ahead, hook, tail, max_wave=0, times=2, collect_stats=True):
     monkeypatch.setenv("HPT_BOUNCE_AHEAD", ahead)
     monkeypatch.setenv("HPT_SCHEDULE_TEST", hook)
     monkeypatch.setenv("HPT_TAIL_PATHS", tail)
     _, r, _ = scene_util.make(name, n, 64, 48, 16, device=0, radii=radii)
     out = []
     for _ in range(times):
-        film = r.render(0, 16, max_wave_paths=max_wave, collect_stats=True)
+        film = r.render(0, 16, max_wave_paths=max_wave, collect_stats=collect_stats)
         out.append((film, r.stats()))
     r.close()
     return out
@@ -79,3 +79,22 @@ def test_bounce_ahead_several_waves(monkeypatch):
     np.testing.assert_array_equal(second, ref)
     assert s2.waves_ahead == s0.waves and s2.schedule_misses == 0
     assert s2.bounces == s0.bounces and s2.tail_paths == s0.tail_paths
+
+
+ROLLED_BACK = ("trace_launches", "packet_launches", "nodes", "prims", "closest_rays", "shadow_rays", "prim_exact",
+               "packet_rays", "binary_nodes")
+
+
+def test_overflow_rollback_accounting(monkeypatch):
+    """A wave rendered again after its schedule overflowed counts once: the timing events and
+    traversal counters (collect_stats=2) of the discarded attempt are rolled back, so the second
+    render of a half-size schedule (one miss) reports the launches and counters of a first
+    render, which reads every queue length back: the same context's, and that of a context
+    without the hook."""
+    (_, plain), _ = _render_twice("furball_marschner", 1500, None, monkeypatch, "1", "0", "2000", collect_stats=2)
+    (_, s1), (_, s2) = _render_twice("furball_marschner", 1500, None, monkeypatch, "1", "1", "2000", collect_stats=2)
+    assert s1.schedule_misses == 0 and s2.schedule_misses == 1
+    assert s2.trace_launches >= 1 and s2.packet_launches == 1 and s2.nodes > 0 and s2.shadow_rays > 0
+    for first in (s1, plain):
+        for k in ROLLED_BACK:
+            assert getattr(s2, k) == getattr(first, k), k
